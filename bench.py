@@ -11,14 +11,19 @@ activations, fp32 weights, fp32 accumulation, exactly as the reference trains
 operand is carried as three bf16 planes (hi + mid + lo, split once where it is produced) and the
 six significant plane products run on the bf16 matrix cores (csrc/kernels/gemm_sp*.hip; measured
 error against fp64 at or below the v_mfma_f32_32x32x2_f32 kernel, tests/test_gemm_sp_gpu.py; the
-same step on that f32-MFMA kernel is reported beside it as ``transformer_fp32_f32mfma``).  Every
+same step on that f32-MFMA kernel is reported beside it as ``transformer_fp32_f32mfma`` by ``--full``).  Every
 model is built after resetting the dropout salt sequence and the torch seed, so its trajectory
 does not depend on which models ran before it in the process; the headline run's per-step losses
-are in ``losses``.  The bf16
+are in ``losses``.  With ``--full`` the bf16
 (fp32-master) variant of the same step and the distributed_cnn workload (the other half of the
 BASELINE metric) are reported beside it for the same N, plus the LSTM / MLP workloads.
 
-Contract: ``python bench.py --gpus N --steps K --warmup W``.  Multi-GPU runs are launched by
+Contract: ``python bench.py --gpus N --steps K --warmup W`` sets up the flagship step, runs W untimed
+warm-up steps and K timed ones and prints the result line: nothing else.  ``--full`` adds everything
+the benchmark measures beside the headline (the bf16 and f32-MFMA variants of the step, ZeRO-1 and
+the collective timings and the ranks-in-sync check when N > 1, the CNN / LSTM / MLP workloads).
+``--dump-outputs DIR`` writes what the last timed step returned to its caller (``dump_outputs``).
+Multi-GPU runs are launched by
 torch.distributed.run (one rank per GPU, RCCL); when ``--gpus N > 1`` is given WITHOUT a
 launcher (no WORLD_SIZE in the environment) this script spawns the N ranks itself before any
 GPU call (reference launch: distributed_cnn.py:227-231, TorchDistributor(num_processes=N)).
@@ -62,7 +67,7 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--model", default="all", choices=["all", "transformer", "cnn", "aux"])
     ap.add_argument("--dtype", default="auto", choices=["auto", "fp32", "bf16", "both"],
-                    help="transformer compute dtype; auto = fp32 headline + bf16 beside it on GPU, fp32 on CPU")
+                    help="transformer compute dtype; auto = the fp32 headline (with --full on GPU: bf16 beside it)")
     ap.add_argument("--device", default="auto", choices=["auto", "cpu", "cuda"])
     ap.add_argument("--aux-steps", type=int, default=100, help="timed steps of the LSTM / MLP extras")
     ap.add_argument("--cnn-batch", type=int, default=32)
@@ -82,6 +87,12 @@ def parse(argv=None):
                     help="skip the ZeRO-1 variant of the fp32 transformer step (measured only when N > 1)")
     ap.add_argument("--no-f32-compare", action="store_true",
                     help="skip the f32-MFMA comparison run of the fp32 transformer step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the other precisions of the step, the "
+                         "CNN / LSTM / MLP workloads, and with N > 1 ZeRO-1, the collectives and the ranks-in-sync check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, per-step losses, updated "
+                         "parameters) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -135,6 +146,33 @@ def fresh_model_state(seed):
     from sparkmi.ops.rng import reset_salts
     reset_salts()
     torch.manual_seed(seed)
+
+
+DUMP_MAX = 1 << 22  # elements per dumped array (16 MB of float32)
+
+
+def dump_positions(numel):
+    """The positions of a ``numel``-element buffer that ``dump_outputs`` samples (sorted, drawn with
+    a fixed seed, so every run and every reader of a dump gets the same ones)."""
+    import torch
+    return torch.randint(0, numel, (DUMP_MAX,), generator=torch.Generator().manual_seed(2024)).sort().values
+
+
+def dump_outputs(dirname, loss, losses, flat):
+    """What a caller of the timed step holds after the last one: its loss (``loss.npy``), every timed
+    step's loss (``losses.npy``) and the parameters the optimizer left (``params.npy``: the flat fp32
+    master buffer, or its elements at ``dump_positions`` when it is larger).  float32 only."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    if losses:
+        every = torch.stack([l.detach().float().reshape(()) for l in losses])
+        np.save(os.path.join(dirname, "losses.npy"), every.cpu().numpy())
+    p = flat.master.detach()
+    if p.numel() > DUMP_MAX:
+        p = p[dump_positions(p.numel()).to(p.device)]
+    np.save(os.path.join(dirname, "params.npy"), p.float().cpu().numpy())
 
 
 def time_steps(runner, batches, steps, warmup, device, world, record=None):
@@ -270,7 +308,7 @@ def time_comm_paths(device, world, bucket_mb, iters=5):
     return out
 
 
-def bench_cnn(args, rank, world, device, dtype="fp32"):
+def bench_cnn(args, rank, world, device, dtype="fp32", dump=None):
     """distributed_cnn.py workload: FashionMNISTModel, batch 32/GPU, SGD lr 0.01, mean CE."""
     import torch
     from sparkmi.data.synthetic import fashion_mnist_like
@@ -296,7 +334,9 @@ def bench_cnn(args, rank, world, device, dtype="fp32"):
     batches = [(imgs[i * args.cnn_batch:(i + 1) * args.cnn_batch], labels[i * args.cnn_batch:(i + 1) * args.cnn_batch])
                for i in range(16)]
     elapsed, loss = time_steps(runner, batches, args.cnn_steps, max(args.warmup, 5), device, world)
-    ar = time_allreduce(flat, device, world)
+    if dump and rank == 0:
+        dump_outputs(dump, loss, None, flat)
+    ar = time_allreduce(flat, device, world) if args.full else None
     comm = None
     if ddp is not None:
         comm = ddp.comm
@@ -433,9 +473,10 @@ def bench_mlp(args, rank, world, device):
             "vs_baseline": round(v / BASELINE_MLP, 2), "config": f"MLP 4-5-4-3 sigmoid, batch 30/GPU, SGD, fp32, dp{world}"}
 
 
-def bench_transformer(args, rank, world, device, dtype, zero=False):
+def bench_transformer(args, rank, world, device, dtype, zero=False, dump=None):
     """One full training step of the BASELINE transformer at ``dtype`` ('fp32' = reference
-    precision, or 'bf16' = bf16 activations/weights with fp32 master weights and fp32 accumulate)."""
+    precision, or 'bf16' = bf16 activations/weights with fp32 master weights and fp32 accumulate).
+    ``dump``: directory for the last timed step's outputs (rank 0)."""
     import torch
     from sparkmi.data.synthetic import copy_pairs, translation_pairs
     from sparkmi.models.transformer import Transformer, transformer_flops_per_sample
@@ -469,13 +510,16 @@ def bench_transformer(args, rank, world, device, dtype, zero=False):
     losses = []
     elapsed, loss = time_steps(runner, batches, args.steps, args.warmup, device, world, record=losses)
     final_loss = float(loss.float().item()) if loss is not None else float("nan")
-    in_sync = ranks_in_sync(flat, world)
-    ar = time_allreduce(flat, device, world)
+    if dump and rank == 0:
+        dump_outputs(dump, loss, losses, flat)
+    # --full: the ranks-in-sync check and the isolated collective timings are runs of their own
+    in_sync = ranks_in_sync(flat, world) if args.full else None
+    ar = time_allreduce(flat, device, world) if args.full else None
     comm = None
     if ddp is not None:
         comm = {"path": ddp.comm, "probe": ddp.comm_probe}
         ddp.close()
-        if dtype == "fp32" and not zero:
+        if dtype == "fp32" and not zero and args.full:
             comm["paths"] = time_comm_paths(device, world, args.bucket_mb)
     value = world * args.batch * args.steps / elapsed
     tflops = transformer_flops_per_sample(args.layers, args.seq, args.vocab) * value / world / 1e12
@@ -513,7 +557,8 @@ def main():
     from sparkmi.parallel import destroy, init_distributed
     rank, world, device = init_distributed()
     if args.dtype == "auto":
-        dtypes = ["fp32", "bf16"] if device.type == "cuda" else ["fp32"]
+        # bf16 beside the fp32 headline is an extra measurement: --full
+        dtypes = ["fp32", "bf16"] if device.type == "cuda" and args.full else ["fp32"]
     elif args.dtype == "both":
         dtypes = ["fp32", "bf16"]
     else:
@@ -540,12 +585,15 @@ def main():
             if int(flag.item()) and err is None:
                 err = "failed on another rank"
         return {"error": err} if err else out
-    if args.model in ("all", "cnn"):
+    cnn_dump = args.dump_outputs if args.model == "cnn" else None
+    if args.full and args.model in ("all", "cnn"):
         # BASELINE's CNN config is bf16 (Conv2d on matrix cores); the fp32 kernel is reported too
-        cnn32 = side(bench_cnn, args, rank, world, device, "fp32")
-        cnn = side(bench_cnn, args, rank, world, device, "bf16") if device.type == "cuda" else cnn32
+        cnn32 = side(bench_cnn, args, rank, world, device, "fp32", None if device.type == "cuda" else cnn_dump)
+        cnn = side(bench_cnn, args, rank, world, device, "bf16", cnn_dump) if device.type == "cuda" else cnn32
         cnn_recipe = side(bench_cnn_recipe, args, rank, world, device, "bf16" if device.type == "cuda" else "fp32")
-    if args.model in ("all", "aux") and not args.no_aux:
+    elif args.model == "cnn":
+        cnn = bench_cnn(args, rank, world, device, "bf16" if device.type == "cuda" else "fp32", cnn_dump)
+    if (args.model == "aux" or (args.model == "all" and args.full)) and not args.no_aux:
         lstm = side(bench_lstm, args, rank, world, device)
         mlp = side(bench_mlp, args, rank, world, device)
     if args.model == "aux":  # LSTM + MLP extras only (profiling)
@@ -565,10 +613,11 @@ def main():
                               "cnn_fp32": cnn32, "cnn_recipe_path": cnn_recipe}))
         destroy()
         return
-    tr = {dt: bench_transformer(args, rank, world, device, dt) for dt in dtypes}
+    tr = {dt: bench_transformer(args, rank, world, device, dt, dump=args.dump_outputs if dt == dtypes[0] else None)
+          for dt in dtypes}
     head = tr[dtypes[0]]
     f32mfma = None
-    if "fp32" in dtypes and device.type == "cuda" and not args.no_f32_compare:
+    if args.full and "fp32" in dtypes and device.type == "cuda" and not args.no_f32_compare:
         # the same fp32 step with every GEMM product on v_mfma_f32_32x32x2_f32 instead of the
         # exact-product bf16 split (both fp32 in / out / accumulate), for comparison
         from sparkmi import _native
@@ -583,7 +632,7 @@ def main():
             C.gemm_f32_algo(prev)
             G.SP = prev_sp
     zero1 = None
-    if world > 1 and "fp32" in dtypes and not args.no_zero_compare:
+    if args.full and world > 1 and "fp32" in dtypes and not args.no_zero_compare:
         # ZeRO-1 beside the headline (reduce-scatter under the backward, sharded Adam, parameter
         # all-gather after it): measured at every N so the replicated-vs-sharded choice rests on data
         zero1 = side(bench_transformer, args, rank, world, device, "fp32", True)

@@ -43,8 +43,33 @@ def test_bench_single_rank():
     assert out["allreduce_ms"] is None
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full the default selection (--model all, --dtype auto) times the flagship step and
+    nothing beside it; --steps is the number of timed steps; --dump-outputs writes the last step's
+    loss, every timed loss and the updated parameters as float32 .npy, from the same inputs every run."""
+    import numpy as np
+    tiny = [a for a in TINY if a not in ("--model", "transformer")]
+    outs = []
+    for d in ("a", "b"):
+        out = _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(tmp_path / d)] + tiny)
+        _check(out, 1)
+        assert not {"cnn", "cnn_fp32", "cnn_recipe_path", "extra", "transformer_bf16", "transformer_fp32_f32mfma",
+                    "transformer_fp32_zero1"} & set(out)
+        assert len(out["losses"]) == 2 and out["ms_per_step"] > 0
+        arrays = {n: np.load(tmp_path / d / f"{n}.npy") for n in ("loss", "losses", "params")}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert arrays["losses"].shape == (2,) and arrays["loss"][0] == arrays["losses"][-1]
+        assert arrays["params"].size > 0 and np.isfinite(arrays["params"]).all()
+        np.testing.assert_allclose(arrays["losses"], out["losses"], atol=1e-4)
+        outs.append(arrays)
+    # same arguments, same inputs: on the CPU the step is deterministic up to the thread count's
+    # summation order
+    for n in outs[0]:
+        np.testing.assert_allclose(outs[0][n], outs[1][n], rtol=1e-4, atol=1e-5)
+
+
 def test_bench_spawns_ranks():
-    out = _run([sys.executable, "bench.py", "--gpus", "2"] + TINY)
+    out = _run([sys.executable, "bench.py", "--gpus", "2", "--full"] + TINY)
     _check(out, 2)
     assert out["allreduce_ms"] is not None and out["transformer_fp32"]["grad_bytes"] > 0
     assert out["transformer_fp32"]["ranks_in_sync"] is True
@@ -57,7 +82,7 @@ def test_bench_two_ranks_on_the_gpu():
     fp32 transformer step through the GPU kernels, split-graph backward with the overlapped
     bucket reduction, and bit-identical parameters on both ranks after the timed steps."""
     out = _run([sys.executable, "bench.py", "--gpus", "2", "--model", "transformer", "--dtype", "fp32", "--layers", "2",
-                "--steps", "4", "--warmup", "3", "--no-f32-compare", "--no-zero-compare"],
+                "--steps", "4", "--warmup", "3", "--full", "--no-f32-compare", "--no-zero-compare"],
                env={"SPARKMI_DIST_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 64 and out["value"] > 0
     assert out["transformer_fp32"]["ranks_in_sync"] is True, out["transformer_fp32"]
@@ -82,7 +107,7 @@ def test_bench_cnn_two_ranks_on_the_gpu():
     round-4 bar of x1.3 assumed the two ranks' kernels would overlap for free, which one shared GPU
     cannot show: the bar here is the measured ratio + 10 %, and the 8-GPU run (one rank per GPU)
     is where the data-parallel overhead is the reduction alone."""
-    base = ["--model", "cnn", "--cnn-steps", "400", "--warmup", "20"]
+    base = ["--model", "cnn", "--cnn-steps", "400", "--warmup", "20", "--full"]
     one = _run([sys.executable, "bench.py", "--gpus", "1"] + base)
     two = _run([sys.executable, "bench.py", "--gpus", "2"] + base, env={"SPARKMI_DIST_BACKEND": "gloo"})
     assert two["n_gpus"] == 2 and two["config"]["global_batch"] == 64

@@ -325,11 +325,14 @@ def test_optimizer_step_counter_many_blocks_graph():
 
 
 def test_transformer_gpu_vs_cpu():
+    import glob
     import os
     from safetensors.torch import load_file
     from sparkmi.models.transformer import Transformer
     from sparkmi.utils.flat import FlatParams
-    gold = load_file(os.path.join(os.path.dirname(__file__), "fixtures", "transformer_ref.safetensors"))
+    parts = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "transformer_ref.*.safetensors")))
+    gold = {k: v for f in parts for k, v in load_file(f).items()}
+    assert {"src", "tgt", "logits", "loss"} <= set(gold), sorted(gold)  # every part found
     sd = {k[len("param."):]: v for k, v in gold.items() if k.startswith("param.")}
     m = Transformer(d_model=128, ffn_hidden=256, num_heads=2, num_layers=2, max_sequence_length=16,
                     src_vocab_size=50, tgt_vocab_size=60)

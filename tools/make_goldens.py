@@ -2,7 +2,8 @@
 """Generate reference-parity golden tensors from the reference's transformer.py.
 
 Run once in the build container (the reference is mounted read-only at /root/reference and is
-NOT available on the GPU box), output is checked in under tests/fixtures/ as safetensors.
+not available where the GPU tests run), output is checked in under tests/golden/ as safetensors
+parts (keys in sorted order, each file below the 1 MiB limit for a committed file).
 The reference module is imported, never copied.  Config: d_model 128, 2 heads (head_dim 64,
 the kernel's), ffn 256, 2 layers, S 16, B 3, vocab 50 -> 60; eval mode (no dropout) with the
 reference's own masks (padding mask, look-ahead mask for decoder self AND cross attention).
@@ -17,7 +18,8 @@ REF = os.environ.get("SPARKMI_REFERENCE", "/root/reference")
 sys.path.insert(0, REF)
 import transformer as ref  # noqa: E402
 
-OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "fixtures")
+OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+PART_BYTES = 900 * 1024
 
 
 def main():
@@ -54,8 +56,17 @@ def main():
     tensors.update({"sdp.q": q, "sdp.k": k, "sdp.v": v, "sdp.out_lookahead": o_la, "sdp.out_padding": o_pm,
                     "pe.table": ref.PositionalEncoding(128, 16)()})
     os.makedirs(OUT, exist_ok=True)
-    save_file({k: v.contiguous() for k, v in tensors.items()}, os.path.join(OUT, "transformer_ref.safetensors"))
-    print("wrote", len(tensors), "tensors")
+    parts, size = [{}], 0
+    for k in sorted(tensors):
+        n = tensors[k].numel() * tensors[k].element_size()
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = tensors[k].contiguous()
+        size += n
+    for i, part in enumerate(parts):
+        save_file(part, os.path.join(OUT, f"transformer_ref.{i:02d}.safetensors"))
+    print("wrote", len(tensors), "tensors in", len(parts), "parts")
 
 
 if __name__ == "__main__":
