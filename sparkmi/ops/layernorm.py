@@ -14,6 +14,7 @@ from . import _grad
 from . import planes as _pl
 from ._grad import grad_buf, grad_ready
 
+LN_BWD_MAX_D = 2048  # csrc/kernels/layernorm.hip: ln_bwd_launch rejects wider rows (ln_fwd_launch: 4096)
 
 def _planes_for(t, D, M):
     """bf16 hi/mid/lo planes [3, M, D] for an fp32 output the split-plane GEMM will consume
@@ -138,6 +139,13 @@ def add_dropout_layernorm(h, residual, gamma, beta, p=0.0, rng=None, salt=0, eps
     if rng is None:
         p = 0.0
         rng = _NULL_RNG
+    D = h.shape[-1]
+    if D > LN_BWD_MAX_D and h.is_cuda and torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in (h, residual, gamma, beta)):
+        # the forward kernel takes D <= 4096, the backward only D <= 2048: refuse here, before
+        # anything is launched, instead of from inside the backward pass
+        raise ValueError(f"layernorm: D = {D} > {LN_BWD_MAX_D} has no backward kernel "
+                         "(forward only, under torch.no_grad())")
     return AddDropoutLayerNorm.apply(h, residual, gamma, beta, float(p), rng, int(salt), float(eps), r_slot)
 
 
