@@ -79,7 +79,6 @@ int smi_gemm_sp(const GemmSpArgs*, hipStream_t);
 int smi_gemm_sp_wgrad_group(const void* const*, const long*, const long*, const void* const*, const long*, const long*,
                             void* const*, void* const*, const int*, const int*, const int*, int, hipStream_t);
 int smi_split3(const float*, long, int, long, void*, long, long, hipStream_t);
-int smi_gemm_sp_waves(int);
 int smi_gemm_sp_tm(int);
 int smi_gemm_sp_wg_tm(int);
 int smi_attn_ae(int);
@@ -483,14 +482,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("split3", [](u x, long rows, int cols, long ldx, u Pp, long ldp, long ps, u st) {
     chk(smi_split3(PF(x), rows, cols, ldx, P(Pp), ldp, ps, S(st)), "split3");
   });
-  m.def("gemm_sp_waves", [](int set) { return smi_gemm_sp_waves(set); },
-        "split-plane GEMM waves per 128x128 tile (4 | 8); other values query");
   m.def("gemm_sp_tm", [](int set) { return smi_gemm_sp_tm(set); },
-        "split-plane GEMM tile form for large problems (16: 256x128 on 16x16x32 MFMA | 256 | 128); other values query");
+        "split-plane GEMM tile form for large problems (16: 256x128 tiles where they fill the chip | 128: 128x128 only); other values query");
   m.def("adam_wide", [](int set) { return smi_adam_wide(set); },
         "Adam launch: 1 = 1024-thread blocks, <= 512 (default), 0 = 256-thread blocks, <= 4096; other values query");
   m.def("gemm_sp_wg_tm", [](int set) { return smi_gemm_sp_wg_tm(set); },
-        "tile form of the grouped weight-gradient launch (128 | 256 | 16; -1 follows gemm_sp_tm); other values query");
+        "tile form of the grouped weight-gradient launch (128 | 16; -1 follows gemm_sp_tm); other values query");
   m.def("gemm_f32_algo", [](int set) { return smi_gemm_f32_algo(set); },
         "fp32 GEMM product algorithm: 0 = f32 MFMA, 6 = 3-way bf16 split (6 terms); set < 0 queries");
   m.def("gemm_f32_wgrad_group", [](std::vector<u> A, std::vector<long> lda, std::vector<u> B, std::vector<long> ldb,

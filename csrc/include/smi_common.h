@@ -229,4 +229,18 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t smi_rsrc(const void* p, int by
   return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, bytes, 0x00020000);
 }
 __device__ __forceinline__ void smi_wt_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// Buffer offset past every descriptor extent the kernels build (< 2^31 bytes): the range check
+// makes such a load return zeros, so ragged edges need no branch.
+#define SMI_OOB 0x7FFFFFF0u
+
+// ---- tile order of the GEMMs ----
+#define SMI_NUM_CU 256
+// XCD-aware bijective remap of workgroup `orig` of `nwg`: consecutive workgroups land on different
+// XCDs (b and b + 8 share one); each XCD gets a contiguous range of tiles, so the tiles sharing
+// an A row-panel share its L2.
+__device__ __forceinline__ int smi_xcd_remap(int orig, int nwg) {
+  if (nwg < 16) return orig;
+  const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+}
 

@@ -35,7 +35,6 @@
 #define FBN 128
 #define FBK 32
 #define KC_PITCH 36  // k-contig LDS row pitch (floats)
-#define NUM_CU 256
 
 template <bool KMAJ, int R>
 struct F32Tile {
@@ -47,7 +46,6 @@ struct F32Tile {
 // Branch-free global -> register staging through a buffer descriptor: out-of-range rows / k read
 // 0 because their offset is pushed past the descriptor's extent (the range check returns zeros),
 // so a k-loop body stays ONE basic block and sched_group_barrier can interleave it.
-#define F32_OOB 0x7FFFFFF0
 template <bool KMAJ, int R>
 __device__ __forceinline__ void f32_bload(__amdgpu_buffer_rsrc_t rs, long ld, int r0, int rlim, int k0, int klim,
                                           float4 (&v)[F32Tile<KMAJ, R>::NV], int tid) {
@@ -57,10 +55,10 @@ __device__ __forceinline__ void f32_bload(__amdgpu_buffer_rsrc_t rs, long ld, in
     int off;
     if (!KMAJ) {
       const int gr = r0 + (f >> 3), gk = k0 + (f & 7) * 4;
-      off = (gr < rlim && gk < klim) ? (int)(((long)gr * ld + gk) * 4) : F32_OOB;
+      off = (gr < rlim && gk < klim) ? (int)(((long)gr * ld + gk) * 4) : (int)SMI_OOB;
     } else {
       const int gk = k0 + f / (R / 4), gc = r0 + (f % (R / 4)) * 4;
-      off = (gk < klim && gc < rlim) ? (int)(((long)gk * ld + gc) * 4) : F32_OOB;
+      off = (gk < klim && gc < rlim) ? (int)(((long)gk * ld + gc) * 4) : (int)SMI_OOB;
     }
     v[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
   }
@@ -91,14 +89,6 @@ __device__ __forceinline__ void f32_frag(const float* __restrict__ lds, int c0, 
 #pragma unroll
     for (int s = 0; s < 16; ++s) f[s] = lds[(16 * h + s) * R + rc];
   }
-}
-
-__device__ __forceinline__ int f32_tile_remap(int orig, int nwg) {
-  // XCD-aware bijective remap: consecutive blocks land on different XCDs (b % 8); give each XCD a
-  // contiguous range of tiles so tiles sharing an A row-panel share its L2
-  if (nwg < 16) return orig;
-  const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
 }
 
 // ---- fp32 products on the bf16 matrix cores (3-way split, 6 product terms) ----
@@ -268,8 +258,7 @@ __device__ __forceinline__ void gemm_f32_tile_pipe(const GemmF32Args& g, int til
   float4 ra0[TA::NV], rb0[TB::NV], ra1[TA::NV], rb1[TB::NV];
   const long a_bytes = 4 * (AK ? (long)(g.K - 1) * g.lda + g.M : (long)(g.M - 1) * g.lda + g.K);
   const long b_bytes = 4 * (BKM ? (long)(g.K - 1) * g.ldb + g.N : (long)(g.N - 1) * g.ldb + g.K);
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)g.A, 0, (int)a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)g.B, 0, (int)b_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = smi_rsrc(g.A, (int)a_bytes), rB = smi_rsrc(g.B, (int)b_bytes);
   // every step is unconditional (tiles past nk load zeros into stages nobody reads): no branches
   auto ld = [&](int t, float4 (&ra)[TA::NV], float4 (&rb)[TB::NV]) {
     f32_bload<AK, BMT>(rA, g.lda, m0, g.M, kbeg + t * FBK, kend, ra, tid);
@@ -301,14 +290,7 @@ __device__ __forceinline__ void gemm_f32_tile_pipe(const GemmF32Args& g, int til
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            acc[i][j] = MF32X16(sa[i].h, sb[j].h, acc[i][j]);
-            cacc[i][j] = MF32X16(sa[i].l, sb[j].h, cacc[i][j]);
-            cacc[i][j] = MF32X16(sa[i].m, sb[j].m, cacc[i][j]);
-            cacc[i][j] = MF32X16(sa[i].h, sb[j].l, cacc[i][j]);
-            cacc[i][j] = MF32X16(sa[i].m, sb[j].h, cacc[i][j]);
-            cacc[i][j] = MF32X16(sa[i].h, sb[j].m, cacc[i][j]);
-          }
+          for (int j = 0; j < 2; ++j) split3_mma2(sa[i], sb[j], acc[i][j], cacc[i][j]);
       }
     } else {
 #pragma unroll
@@ -382,6 +364,8 @@ __device__ __forceinline__ void gemm_f32_tile_pipe(const GemmF32Args& g, int til
 // fragments (one ds_read_b128 per plane per 16-deep block).  Staging thread map: each thread
 // owns 4 consecutive k of a row — a float4 for a k-contiguous operand, four coalesced dword
 // loads (adjacent lanes = adjacent rows) for a k-major one, so the transposition is free.
+// (The plane images below are the ones of smi_plane_lds.h, kept as this path's own copy: with the
+// shared definitions the compiler allocates the XS = 2 dgrad kernels 185 AGPRs instead of 166.)
 // LDS plane: [128 rows][32 k] bf16, 64-B rows, 16-B chunk index XOR-swizzled with (row >> 2) & 3
 // (the 16 rows a ds_read_b128 quarter-wave touches land on 16 distinct bank quads); stage =
 // 2 operands x 3 planes x 8 KiB = 48 KiB, 3 stages.
@@ -412,10 +396,10 @@ __device__ __forceinline__ void xs_bload(__amdgpu_buffer_rsrc_t rs, long ld, int
     int off;
     if (!KMAJ) {
       const int gr = r0 + (f >> 3), gk = k0 + (f & 7) * 4;
-      off = (gr < rlim && gk < klim) ? (int)(((long)gr * ld + gk) * 4) : F32_OOB;
+      off = (gr < rlim && gk < klim) ? (int)(((long)gr * ld + gk) * 4) : (int)SMI_OOB;
     } else {
       const int gk = k0 + (f >> 5), gc = r0 + (f & 31) * 4;
-      off = (gk < klim && gc < rlim) ? (int)(((long)gk * ld + gc) * 4) : F32_OOB;
+      off = (gk < klim && gc < rlim) ? (int)(((long)gk * ld + gc) * 4) : (int)SMI_OOB;
     }
     v[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
   }
@@ -491,8 +475,7 @@ __device__ __forceinline__ void gemm_xs_tile(const GemmF32Args& g, int tile, int
   float bsum[4] = {0.f, 0.f, 0.f, 0.f};  // AK: partial row sums of A rows (tid & 31) * 4 + j
   const long a_bytes = 4 * (AK ? (long)(g.K - 1) * g.lda + g.M : (long)(g.M - 1) * g.lda + g.K);
   const long b_bytes = 4 * (BKM ? (long)(g.K - 1) * g.ldb + g.N : (long)(g.N - 1) * g.ldb + g.K);
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)g.A, 0, (int)a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)g.B, 0, (int)b_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = smi_rsrc(g.A, (int)a_bytes), rB = smi_rsrc(g.B, (int)b_bytes);
   float4 ra0[4], rb0[4], ra1[4], rb1[4];
   auto ld = [&](int t, float4 (&ra)[4], float4 (&rb)[4]) {
     xs_bload<AK>(rA, g.lda, m0, g.M, kbeg + t * FBK, kend, ra, tid);
@@ -518,14 +501,7 @@ __device__ __forceinline__ void gemm_xs_tile(const GemmF32Args& g, int tile, int
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        acc[i][j] = MF32X16(sa[i].h, sb[j].h, acc[i][j]);
-        cacc[i][j] = MF32X16(sa[i].l, sb[j].h, cacc[i][j]);
-        cacc[i][j] = MF32X16(sa[i].m, sb[j].m, cacc[i][j]);
-        cacc[i][j] = MF32X16(sa[i].h, sb[j].l, cacc[i][j]);
-        cacc[i][j] = MF32X16(sa[i].m, sb[j].h, cacc[i][j]);
-        cacc[i][j] = MF32X16(sa[i].h, sb[j].m, cacc[i][j]);
-      }
+      for (int j = 0; j < 2; ++j) split3_mma2(sa[i], sb[j], acc[i][j], cacc[i][j]);
   };
   constexpr int NVM = (AK ? 16 : 4) + (BKM ? 16 : 4);  // global load instructions per k-tile
   // one half-iteration: [block 0 MFMAs | global loads of t+3, block-1 fragment reads, split +
@@ -606,7 +582,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32_pipe_kernel(GemmF32Args g) {
   float smem[XS == 2 ? XS_SMEM_FLOATS : 3 * (F32Tile<AK, 128>::ELEMS + F32Tile<BKM, FBN>::ELEMS)];
   const int nwg = ((g.M + 127) / 128) * ((g.N + FBN - 1) / FBN);
   const int split = blockIdx.x / nwg;
-  const int tile = f32_tile_remap(blockIdx.x - split * nwg, nwg);
+  const int tile = smi_xcd_remap(blockIdx.x - split * nwg, nwg);
   if constexpr (XS == 2) gemm_xs_tile<AK, BKM, EPI>(g, tile, split, smem);
   else gemm_f32_tile_pipe<AK, BKM, EPI, XS>(g, tile, split, smem);
 }
@@ -641,7 +617,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32_wgrad_group_kernel(WgradGroup
   const int nwg = ((g.M + 127) / 128) * ((g.N + FBN - 1) / FBN);
   const int lt = t - gr.t0[e];
   if (lt >= nwg) return;  // padding
-  if constexpr (XS == 2) gemm_xs_tile<true, true, FE_ACC>(g, f32_tile_remap(lt, nwg), 0, smem);
-  else gemm_f32_tile_pipe<true, true, FE_ACC, XS>(g, f32_tile_remap(lt, nwg), 0, smem);  // lt >= nwg: padding
+  if constexpr (XS == 2) gemm_xs_tile<true, true, FE_ACC>(g, smi_xcd_remap(lt, nwg), 0, smem);
+  else gemm_f32_tile_pipe<true, true, FE_ACC, XS>(g, smi_xcd_remap(lt, nwg), 0, smem);  // lt >= nwg: padding
 }
 

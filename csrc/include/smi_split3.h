@@ -23,6 +23,17 @@ __device__ __forceinline__ Split3 split3_8(const float* f) {
   return r;
 }
 #define MF32X16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
+// a . b on two accumulators: hi.hi into acc (the rounding sequence of a plain fp32 chain), the five
+// correction products lo.hi, mid.mid, hi.lo, mid.hi, hi.mid into cacc (added to acc once, after
+// the k-loop); the dropped mid.lo / lo.mid / lo.lo terms are below one fp32 rounding of the product
+__device__ __forceinline__ void split3_mma2(const Split3& a, const Split3& b, f32x16_t& acc, f32x16_t& cacc) {
+  acc = MF32X16(a.h, b.h, acc);
+  cacc = MF32X16(a.l, b.h, cacc);
+  cacc = MF32X16(a.m, b.m, cacc);
+  cacc = MF32X16(a.h, b.l, cacc);
+  cacc = MF32X16(a.m, b.h, cacc);
+  cacc = MF32X16(a.h, b.m, cacc);
+}
 
 // acc += x . y over a chain of T f32-MFMA steps (v_mfma_f32_32x32x2_f32 takes x[t], y[t] from lane
 // half h as k = (h, t)); the split form regroups 8 consecutive steps into one 32x32x16 block

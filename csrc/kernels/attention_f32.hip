@@ -33,6 +33,7 @@
 #include "smi_common.h"
 #include "smi_attention.h"
 #include "smi_attn_mask.h"
+#include "smi_plane_lds.h"
 #include "smi_split3.h"
 
 #define FCH 32    // rows per streamed chunk (= one 32-row MFMA block)
@@ -508,7 +509,6 @@ __global__ __launch_bounds__(256, XS ? 1 : 2) void attn_f32_dkdv_kernel(AttnF32A
 // registers.
 #define AS_PL (32 * 64)
 #define AS_OP (3 * AS_PL)
-typedef __attribute__((ext_vector_type(4))) short as_s16x4_t;
 
 __device__ __forceinline__ int as_sw(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
 __device__ __forceinline__ int as_off(int r, int c) { return r * 64 + ((((c >> 3) ^ as_sw(r)) & 7) << 3) + (c & 7); }
@@ -567,17 +567,7 @@ __device__ __forceinline__ Split3 as_colfrag(const unsigned short* img, int lane
   const int i = lane & 15, q = i >> 2, p = i & 3, g = lane >> 4;
   const int col = 32 * dt + 16 * (g & 1) + 4 * p;
   const int r0 = 16 * t + 4 * (g >> 1) + q;
-  const int o0 = as_off(r0, col), o1 = as_off(r0 + 8, col);
-  Split3 r;
-  bf16x8_t* outs[3] = {&r.h, &r.m, &r.l};
-#pragma unroll
-  for (int pl = 0; pl < 3; ++pl) {
-    const unsigned short* b = img + pl * AS_PL;
-    const as_s16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) as_s16x4_t*)(b + o0));
-    const as_s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) as_s16x4_t*)(b + o1));
-    *outs[pl] = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-  }
-  return r;
+  return lds_read_tr8x3(img, AS_PL, as_off(r0, col), as_off(r0 + 8, col));
 }
 // acc += a . b, six slice products smallest first (the XS = 1 chains' order)
 __device__ __forceinline__ f32x16_t as_mma(const Split3& a, const Split3& b, f32x16_t acc) {
@@ -1161,14 +1151,7 @@ __global__ __launch_bounds__(512, 1) void attn_sp_bwd8_kernel(AttnF32Args a) {
       Split3 kt[2];
       float4 u[2][2];
       auto ldq = [&](int kw, int sl) {
-        bf16x8_t* outs[3] = {&kt[sl].h, &kt[sl].m, &kt[sl].l};
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-          const unsigned short* bp = Ko[kw] + pl * AS_PL;
-          const as_s16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) as_s16x4_t*)(bp + o0));
-          const as_s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) as_s16x4_t*)(bp + o1));
-          *outs[pl] = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
+        kt[sl] = lds_read_tr8x3(Ko[kw], AS_PL, o0, o1);
         u[sl][0] = *(const float4*)(srow + 32 * kw);
         u[sl][1] = *(const float4*)(srow + 32 * kw + 4);
       };

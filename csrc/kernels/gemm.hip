@@ -51,7 +51,6 @@ __device__ unsigned long long* g_gemm_stamps;
 #define GSTAMP(slot) do {} while (0)
 #endif
 #define TILE_ELEMS (BM * BKK)  // 8192 bf16 = 16 KiB per operand per stage
-#define NUM_CU 256
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
@@ -182,11 +181,7 @@ __device__ __forceinline__ TileInfo tile_of(const GemmArgs& g, int t, int ntn, i
   // t enumerates (split, tile); XCD-aware bijective remap inside one split's tile set
   const int split = t / nwg;
   const int orig = t - split * nwg;
-  int wgid = orig;
-  if (nwg >= 16) {
-    const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  }
+  const int wgid = smi_xcd_remap(orig, nwg);
   TileInfo ti;
   ti.m0 = (wgid / ntn) * bm;
   ti.n0 = (wgid % ntn) * BN;
@@ -215,8 +210,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int t, unsign
   const bool ragged = (g.K % BKK) != 0 || (g.K % g.k_per_split) != 0;
   const uint32_t seed = smi_seed(g.seedp, g.salt);
   const EpiFlags ef = epi_flags<EPI>(g);
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)g.A, 0, (int)g.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)g.B, 0, (int)g.b_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = smi_rsrc(g.A, (int)g.a_bytes), rB = smi_rsrc(g.B, (int)g.b_bytes);
 
     GSTAMP(0);
     const TileInfo ti = tile_of(g, t, ntn, nwg, BMT);
@@ -541,7 +535,7 @@ extern "C" int smi_gemm(const GemmArgs* args, hipStream_t st) {
   // ring depth: 2 stages (2-3 WGs per CU) everywhere by default — measured: 3 or 4 stages
   // (fewer WGs per CU) were 3-5 % slower per step, for WGRAD too.
   const int ns = ak ? 2 : GEMM_NS;
-  const int maxg = NUM_CU * (ns == 2 ? (bm == 64 ? 3 : 2) : (ns == 3 && bm == 64 ? 2 : 1));
+  const int maxg = SMI_NUM_CU * (ns == 2 ? (bm == 64 ? 3 : 2) : (ns == 3 && bm == 64 ? 2 : 1));
   const int grid = ntiles < maxg ? ntiles : maxg;
   const bool atomic = g.out_f32 && g.atomic;
 
@@ -793,7 +787,7 @@ extern "C" int smi_gemm_wgrad_group(const void* const* A, const long* lda, const
   }
   gr.t0[count] = tot;
   gr.count = count;
-  const int grid = tot < 2 * NUM_CU ? tot : 2 * NUM_CU;
+  const int grid = tot < 2 * SMI_NUM_CU ? tot : 2 * SMI_NUM_CU;
   hipLaunchKernelGGL(gemm_wgrad_group_kernel, dim3(grid), dim3(256), 0, st, gr);
   SMI_CHECK_LAUNCH();
 }

@@ -1,29 +1,4 @@
-// fp32 GEMM on the fp32-input matrix cores (v_mfma_f32_32x32x2_f32: exact f32 products and an
-// f32 fmaf accumulation chain, 64 FLOP/clk/SIMD = 157 TF dense) with the same fused epilogues as
-// the bf16 GEMM — the REFERENCE-PRECISION path of every Linear of the reference models
-// (transformer.py:71-72,107-117,175-176,271 run in fp32 by pytorch_machine_translator.py:120-137):
-//
-//   FWD   C[M,N]  = X[M,K] . W[N,K]^T  (+bias, ReLU, dropout)        A k-contig, B k-contig
-//   DGRAD dX[M,K] = dY[M,N] . W[N,K]   (+residual, x relu'/dropout)  A k-contig, B k-major
-//   WGRAD dW[N,K] += dY[M,N]^T . X[M,K] (+ bias grad = dY^T 1)       A k-major,  B k-major
-//
-// CDNA4 design.  The f32 MFMA runs at 1/16 of the bf16 rate, so this kernel is matrix-core bound
-// by a wide margin (a 32-deep k-tile of a 128 x 128 tile = 64 MFMAs = 4096 cycles per
-// SIMD against 32 KiB of L2 -> LDS traffic per workgroup): everything else is arranged so the
-// MFMA pipe never idles —
-//  * 256-thread workgroups (2 x 2 waves), BN = 128, BM = 64 or 128 (a wave owns 32*FM x 64 =
-//    FM x 2 accumulators of 32 x 32), two workgroups per CU so one's barrier / epilogue overlaps
-//    the other's MFMAs;
-//  * register-staged double buffering: the next k-tile's float4 global loads are issued before
-//    the current k-tile's MFMAs and written to the other LDS buffer after them — one barrier
-//    per k-tile, global latency hidden under 2-4 k us of matrix work;
-//  * k-permuted fragments: lane half h of a 32x32x2 MFMA supplies k = 16h + s at step s, so a
-//    k-contiguous operand is read as four ds_read_b128 per 16 steps from an LDS image with a
-//    36-float row pitch (conflict-free for the ds_read_b128 lane groups), and a k-major operand
-//    as ds_read_b32 rows (32 consecutive floats per half-wave: conflict-free, no transpose);
-//  * XCD-aware tile order (tiles sharing an A row-panel run on one XCD's L2).
-// The accumulator layout (col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)) gives each
-// store instruction two full 128-B row segments.
+// fp32 GEMM, FORWARD instances and the launcher; the design is described in smi_gemm_f32_impl.h.
 #include "smi_gemm_f32_impl.h"
 
 // fp32 product algorithm: 0 = f32 MFMA (v_mfma_f32_32x32x2_f32), 6 = 3-way bf16 split, 6 terms

@@ -5,41 +5,35 @@
 
 #include <stdlib.h>
 
-static int g_sp_waves = 8;  // waves per 128 x 128 tile (gemm_sp_waves sets 4 for A/B runs)
-int smi_sp_waves() { return g_sp_waves; }
-// tile form of the large problems: 16 = 256 x 128 on the 16x16x32 MFMA (default), 256 = the same
-// on 32x32x16, 128 = 128 x 128 tiles (a 4-wave software-pipelined 256 x 128 form measured 157 vs
-// 181-187 TF and was removed in round 5)
-static int sp_tm_env() {  // SMI_SP_TM = 16 | 256 | 128 (profiling A/Bs of whole runs); default 16
+// tile form of the large problems: 16 = 256 x 128 tiles on the 16x16x32 MFMA where they fill the
+// chip (default), 128 = 128 x 128 tiles everywhere.  (Removed after losing their measurements: the
+// 256 x 128 tile on the 32x32x16 MFMA, a 4-wave 128 x 128 tile and a 4-wave software-pipelined
+// 256 x 128 form — docs/PERF_NOTES.md.)
+static int sp_tm_env() {  // SMI_SP_TM = 16 | 128 (profiling A/Bs of whole runs); default 16
   const char* e = getenv("SMI_SP_TM");
   const int v = e ? atoi(e) : 16;
-  return (v == 128 || v == 256 || v == 16) ? v : 16;
+  return (v == 128 || v == 16) ? v : 16;
 }
 static int g_sp_tm = sp_tm_env();
 int smi_sp_tm() { return g_sp_tm; }
-// set 128 / 256 / 16 for A/B runs in one process; other values query
+// set 128 / 16 for A/B runs in one process; other values query
 extern "C" int smi_gemm_sp_tm(int set) {
-  if (set == 128 || set == 256 || set == 16) g_sp_tm = set;
+  if (set == 128 || set == 16) g_sp_tm = set;
   return smi_sp_tm();
 }
-// the grouped weight-gradient launch's tile (gemm_sp_wg_tm = 128 | 256 | 16 | 4; default: follow
-// smi_sp_tm).  Per backward the group holds every layer's weight gradients, each a long
-// K = tokens reduction: fewer, larger tiles can leave CUs idle where 128-row tiles fill them.
-// -1 (default): follow smi_sp_tm; 128 / 256 / 16: forced.  128-row tiles for the encoder's
-// 1.5-wave group (384 tiles of 256 x 128 on 256 CUs) measured +0.18 ms per fp32 step
-// (profiles/r5_ab_wgrad_group_tile.log): the 256-row tile's higher efficiency outweighs the
-// half-empty second wave.
+// the grouped weight-gradient launch's tile (gemm_sp_wg_tm = 128 | 16 | -1).  Per backward the
+// group holds every layer's weight gradients, each a long K = tokens reduction: fewer, larger
+// tiles can leave CUs idle where 128-row tiles fill them.  -1: follow smi_sp_tm; 128 / 16: forced.
+// 128-row tiles for the encoder's 1.5-wave group (384 tiles of 256 x 128 on 256 CUs) measured
+// +0.18 ms per fp32 step (profiles/r5_ab_wgrad_group_tile.log): the 256-row tile's higher
+// efficiency outweighs the half-empty second wave.
 static int g_sp_wg_tm = 16;  // (16 = the default sp_tm; pinned so an sp_tm A/B leaves the group alone)
 int smi_sp_wg_tm() {
   return g_sp_wg_tm > 0 ? g_sp_wg_tm : smi_sp_tm();
 }
 extern "C" int smi_gemm_sp_wg_tm(int set) {
-  if (set == 128 || set == 256 || set == 16 || set == -1) g_sp_wg_tm = set;
+  if (set == 128 || set == 16 || set == -1) g_sp_wg_tm = set;
   return smi_sp_wg_tm();
-}
-extern "C" int smi_gemm_sp_waves(int set) {  // set 4 / 8 (A/B runs in one process); other values query
-  if (set == 4 || set == 8) g_sp_waves = set;
-  return smi_sp_waves();
 }
 
 int smi_sp_launch_dgrad(const GemmSpArgs& g, int epi, int out, dim3 grid, bool t256, hipStream_t st);
@@ -98,31 +92,23 @@ extern "C" int smi_gemm_sp(const GemmSpArgs* args, hipStream_t st) {
   if (g.beta_acc) epi |= SE_ACC;
   if (g.mode == 1) return smi_sp_launch_dgrad(g, epi, out, grid, t256, st);  // csrc/kernels/gemm_sp_dgrad.hip
   if (g.mode == 2) return smi_sp_launch_wgrad(g, epi, grid, st);       // csrc/kernels/gemm_sp_wgrad.hip
-  const bool w8 = smi_sp_waves() == 8;
   // the feature sets the models use (anything else: the caller falls back to gemm_f32):
   // fp32 output, or fp32 output + planes (the FFN hidden activation, consumed by linear2)
   if (g.relu > 1 || (!g.C && out != (SO_P | SO_M))) return -1;
-#define SPF(E, O)                                                                                   \
-  do {                                                                                              \
-    if (t256 && smi_sp_tm() == 16) hipLaunchKernelGGL((gemm_sp256m_kernel<false, false, E, O>), grid, dim3(512), 0, st, g); \
-    else if (t256) hipLaunchKernelGGL((gemm_sp256_kernel<false, false, E, O>), grid, dim3(512), 0, st, g); \
-    else if (w8) hipLaunchKernelGGL((gemm_sp_kernel<8, false, false, E, O>), grid, dim3(512), 0, st, g); \
-    else hipLaunchKernelGGL((gemm_sp_kernel<4, false, false, E, O>), grid, dim3(256), 0, st, g);    \
-  } while (0)
-#define SPF_OUT(E)                  \
-  do {                              \
-    if (out == SO_C) SPF(E, SO_C);  \
-    else if (out == (SO_C | SO_P)) SPF(E, SO_C | SO_P); \
-    else return -1;                 \
-  } while (0)
   // the FFN hidden activation: planes for linear2's GEMMs + the positivity mask for its dgrad
   // epilogue, no fp32 tensor (sparkmi/ops/linear.py FFNFn)
   if (out == (SO_P | SO_M)) {
-    if (epi == (SE_BIAS | SE_RELU | SE_DROP)) SPF(SE_BIAS | SE_RELU | SE_DROP, SO_P | SO_M);
-    else if (epi == (SE_BIAS | SE_RELU)) SPF(SE_BIAS | SE_RELU, SO_P | SO_M);
+    if (epi == (SE_BIAS | SE_RELU | SE_DROP)) sp_launch<false, SE_BIAS | SE_RELU | SE_DROP, SO_P | SO_M>(g, grid, t256, st);
+    else if (epi == (SE_BIAS | SE_RELU)) sp_launch<false, SE_BIAS | SE_RELU, SO_P | SO_M>(g, grid, t256, st);
     else return -1;
     SMI_CHECK_LAUNCH();
   }
+#define SPF_OUT(E)                                                                    \
+  do {                                                                                \
+    if (out == SO_C) sp_launch<false, E, SO_C>(g, grid, t256, st);                    \
+    else if (out == (SO_C | SO_P)) sp_launch<false, E, SO_C | SO_P>(g, grid, t256, st); \
+    else return -1;                                                                   \
+  } while (0)
   switch (epi) {
     case 0: SPF_OUT(0); break;
     case SE_BIAS: SPF_OUT(SE_BIAS); break;
@@ -131,6 +117,5 @@ extern "C" int smi_gemm_sp(const GemmSpArgs* args, hipStream_t st) {
     default: return -1;
   }
 #undef SPF_OUT
-#undef SPF
   SMI_CHECK_LAUNCH();
 }

@@ -10,7 +10,7 @@
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
 
 int main(int argc, char** argv) {
-  const int M = 8192, N = argc > 1 ? atoi(argv[1]) : 512, nw = argc > 2 ? atoi(argv[2]) : 8;
+  const int M = 8192, N = argc > 1 ? atoi(argv[1]) : 512;
   const int Ks[] = {64, 128, 256, 512, 1024, 2048};
   const int Kmax = 2048;
   std::vector<unsigned short> h((size_t)3 * M * Kmax);
@@ -39,8 +39,7 @@ int main(int argc, char** argv) {
     g.M = M; g.N = N; g.K = K; g.C = C; g.ldc = N; g.bias = bias; g.dscale = 1.f;
     g.a_bytes = 2 * ((M - 1) * K + K); g.b_bytes = 2 * ((N - 1) * K + K);
     auto launch = [&]() {
-      if (nw == 8) hipLaunchKernelGGL((gemm_sp_kernel<8, false, false, SE_BIAS, SO_C>), dim3(nwg), dim3(512), 0, 0, g);
-      else hipLaunchKernelGGL((gemm_sp_kernel<4, false, false, SE_BIAS, SO_C>), dim3(nwg), dim3(256), 0, 0, g);
+      hipLaunchKernelGGL((gemm_sp_kernel<false, false, SE_BIAS, SO_C>), dim3(nwg), dim3(SP_NT), 0, 0, g);
     };
     for (int it = 0; it < 3; ++it) launch();
     CK(hipDeviceSynchronize());
@@ -62,9 +61,9 @@ int main(int argc, char** argv) {
     }
     const double us = ms * 1000.0 / reps;
     const double fl = 2.0 * M * N * K;
-    printf("waves=%d K=%5d N=%d kernel %.1f us (%.0f TF)  last launch span %.1f us | per-WG avg us: prologue %.2f  kloop %.2f "
+    printf("K=%5d N=%d kernel %.1f us (%.0f TF)  last launch span %.1f us | per-WG avg us: prologue %.2f  kloop %.2f "
            "(%.3f per k-step)  epi-stage %.2f  epi-store %.2f\n",
-           nw, K, N, us, fl / (us * 1e-6) / 1e12, (t4max - t0min) / 100.0, ph[0] / nwg / 100.0, ph[1] / nwg / 100.0,
+           K, N, us, fl / (us * 1e-6) / 1e12, (t4max - t0min) / 100.0, ph[0] / nwg / 100.0, ph[1] / nwg / 100.0,
            ph[1] / nwg / 100.0 / (K / 32), ph[2] / nwg / 100.0, ph[3] / nwg / 100.0);
   }
   return 0;
